@@ -14,10 +14,14 @@ pos [N,2]; inputs resident in HBM before the timed region.  One step = entity ma
 forward(pretrain) + backward of diffusion_loss (+ RCCL all-reduce of the flat gradient buffer when
 N > 1) + AdamW step.  fp32 throughout.
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` (dominant kernel, HIP events on the
-launch stream inside the timed region), `gather_roofline` (the north star's message-passing
-gather at 10k x 768), `cpu_baseline` (the CPU oracle = port of the reference path, timed on the
-host cores on a bounded sample; rank 0, N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the
+headline (`value`, `ms_per_step`, `dtype`, `config`; `per_rank` and `gradient_exchange` when N > 1).
+`--full` adds the measurements beside it, each after the timed region: `roofline` (dominant kernel,
+HIP events around eager launches of the same step), `sustained`, `raster_positions`, `strict_fp32`,
+`gather_roofline` (the north star's message-passing gather at 10k x 768), `projection_roofline`,
+`cpu_baseline` (the CPU oracle = port of the reference path, timed on the host cores on a bounded
+sample; rank 0, N=1 only) and `sample_loop`; the --no-* switches and --sustain-seconds select among
+them.  `--dump-outputs DIR` writes what the last timed step computed as .npy files (dump_outputs).
 """
 from __future__ import annotations
 
@@ -381,6 +385,34 @@ def sample_loop_bench(model, dev, rows=10000, reps=5):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, model, loss, with_grads=True):
+    """`--dump-outputs DIR`: what the timed path left its caller after the LAST timed step, as float32 .npy files: the step's loss
+    (`loss.npy`), the parameters its AdamW step wrote (`parameters.npy`) and the gradients that step applied (`gradients.npy`, zeros
+    for a parameter without one), the last two flattened and concatenated in `model.named_parameters()` order.  When both vectors
+    together would exceed DUMP_BUDGET_BYTES, both hold the same fixed sample of positions (a generator seeded with 0, in ascending
+    order).  The inputs are seeded (model, batch, masking and dropout draws), so two runs with the same arguments -- of this build or
+    another -- can be compared file for file.  `with_grads=False` leaves out the gradients (the mixed stream on one rank: `param.grad`
+    is the buffer of the layout recorded last, not necessarily the last step's)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    ps = [p for _, p in model.named_parameters()]
+    flat = {"parameters": torch.cat([p.detach().reshape(-1).float() for p in ps])}
+    if with_grads:
+        flat["gradients"] = torch.cat([(p.grad.detach() if p.grad is not None else torch.zeros_like(p)).reshape(-1).float() for p in ps])
+    n = flat["parameters"].numel()
+    keep = (DUMP_BUDGET_BYTES - 4096) // (4 * len(flat))      # float32 elements per vector (4 KiB left for the loss and the .npy headers)
+    if n > keep:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values.to(flat["parameters"].device)
+        flat = {k: v[idx] for k, v in flat.items()}
+    arrays = dict(loss=loss.detach().float().reshape(1), **flat)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    return {name: tuple(t.shape) for name, t in arrays.items()}
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher around it: start the N ranks as FRESH child processes through
     `python -m torch.distributed.run` (one process per GPU, rendezvous on 127.0.0.1 at a port found free by bind(0)), hand rank 0's
@@ -448,6 +480,12 @@ def main():
     ap.add_argument("--batch", type=int, default=PER_GPU_BATCH, help="slides per GPU")
     ap.add_argument("--nodes", type=int, default=NODES)
     ap.add_argument("--edges", type=int, default=EDGES)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything beside the headline: the per-kernel roofline (eager launches of "
+                         "the same step), `sustained`, the raster-positions and strict-fp32 legs, the gather and projection microbenchmarks, "
+                         "the CPU baseline and the denoise loop (the --no-* switches and --sustain-seconds select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the loss, parameters and gradients of the last timed step to DIR/*.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--no-strict", action="store_true", help="skip the strict-fp32-attention leg")
@@ -469,13 +507,15 @@ def main():
                          "by row at PITCH pixels (what the reference's preprocessing stores); with temperature 1 all but a band of the "
                          "attention's block pairs are exact zeros and the zero-block map walks them over; reported under config.workload")
     ap.add_argument("--sustain-seconds", type=float, default=6.0,
-                    help="N=1 only: after the timed K steps, keep replaying the same step for this many seconds and report the rate as "
+                    help="--full, N=1 only: after the timed K steps, keep replaying the same step for this many seconds and report the rate as "
                          "`sustained` (steady-state clocks; also gives an external GPU-activity sampler a window of pure GPU work well "
                          "before the CPU baseline starts); 0 switches it off")
     ap.add_argument("--eager", action="store_true",
                     help="launch every kernel of the step from the host instead of replaying the step from HIP graphs "
                          "(training.GraphedPretrainStep, the default for the fixed-shape headline workload)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.eager or args.mixed:
         # eager launches: kernel arguments in device memory (+4-5 % when the step is GPU-bound; it costs host time per launch, so
         # it is not forced on steps of tiny graphs, and a recorded step does not care).  Read by the HIP runtime at its first call.
@@ -639,7 +679,7 @@ def main():
     TSTAT = "mean" if stream is not None else "median"      # fixed shapes: the median launch (robust against one host hiccup); mixed stream: total / count
     graphed = step is not eager_step
     live_sink = None
-    if not graphed:
+    if not graphed and args.full:
         ops.TIMERS.start(timed)
         ops.ATTN_SKIP_MAP_SINK = live_sink = []      # a list append per attention call; the maps are counted after the timed region
     t0 = time.perf_counter()
@@ -653,8 +693,10 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     ops.ATTN_SKIP_MAP_SINK = None
+    if args.dump_outputs and rank == 0:      # before anything below runs the step again
+        dump_outputs(args.dump_outputs, model, loss, with_grads=stream is None or reducer is not None)
     eager_timed_steps = args.steps
-    if graphed and (stream is None or world == 1):     # (the mixed stream's extra eager pass: one rank only -- N > 1 reports no roofline)
+    if args.full and graphed and (stream is None or world == 1):     # (the mixed stream's extra eager pass: one rank only -- N > 1 reports no roofline)
         # kernels launched by a graph replay cannot be bracketed by events: the per-kernel durations of the roofline come
         # from eager launches of the same step right after the timed region (same kernels, same shapes, same clocks); the mixed
         # stream runs each of its layouts once.  The zero-block maps of those launches are kept: the roofline counts the scores
@@ -683,7 +725,7 @@ def main():
         pairs = {"attn_fwd": f / max(t, 1), "attn_bwd_fused": b / max(t, 1), "scores_all": t, "scores_forward": f, "scores_backward": b,
                  "attention_calls": len(live_sink)}
     sustained = None
-    if world == 1 and args.sustain_seconds > 0:
+    if args.full and world == 1 and args.sustain_seconds > 0:
         n_s = max(args.steps, int(args.sustain_seconds / max(dt / args.steps, 1e-4)) + 1)
         torch.cuda.synchronize(); t1 = time.perf_counter()
         for _ in range(n_s):
@@ -698,7 +740,7 @@ def main():
     # positions the input buffers hold) walks those block pairs over.  The positions are written into the recording's input buffer,
     # the step replayed, the synthetic positions restored.
     raster = None
-    if world == 1 and graphed and stream is None and not args.large and args.pixel_positions == 0 and not args.no_raster:
+    if args.full and world == 1 and graphed and stream is None and not args.large and args.pixel_positions == 0 and not args.no_raster:
         import copy
         import math as _m
         from dgdm_histopath_lab_amd.training import GraphedPretrainStep
@@ -741,7 +783,8 @@ def main():
     # the same step at the reference's own arithmetic (fp32 operands on the fp32 matrix instructions, in the attention and in every
     # dense layer): measured here, in the same process on the same box, so the two numbers are comparable
     strict = None
-    if world == 1 and stream is None and not args.large and not args.eager and not args.no_strict and ops.ATTN_PRECISION == "fp16x2":
+    if (args.full and world == 1 and stream is None and not args.large and not args.eager and not args.no_strict
+            and ops.ATTN_PRECISION == "fp16x2"):
         from dgdm_histopath_lab_amd.training import GraphedPretrainStep
         prev = ops.configure(attention="fp32", gemm="fp32")
         try:
@@ -877,13 +920,15 @@ def main():
 
         ev_note = ("HIP events around eager launches of the same step right after the timed region (a graph replay cannot carry events)"
                    if graphed else "HIP events inside the timed region")
-        roofline = attention_roofline(timers, k16 if split else k32, split, ev_note,
-                                      None if split else PMC_VALU_FP32, None if split else PMC_TRAFFIC_FP32,
-                                      timed_steps=(eager_timed_steps if graphed else args.steps), live=pairs if split else None,
-                                      pmc=not args.mixed and args.pixel_positions == 0)
-        if args.mixed:
-            roofline["note"] = ("mixed-size stream: FLOP and duration are means over the stream's layouts (each run once, eagerly, after the timed "
-                                "region); no PMC pass is committed for this workload (traffic / valu_pmc null)")
+        roofline = None
+        if args.full:
+            roofline = attention_roofline(timers, k16 if split else k32, split, ev_note,
+                                          None if split else PMC_VALU_FP32, None if split else PMC_TRAFFIC_FP32,
+                                          timed_steps=(eager_timed_steps if graphed else args.steps), live=pairs if split else None,
+                                          pmc=not args.mixed and args.pixel_positions == 0)
+            if args.mixed:
+                roofline["note"] = ("mixed-size stream: FLOP and duration are means over the stream's layouts (each run once, eagerly, after the "
+                                    "timed region); no PMC pass is committed for this workload (traffic / valu_pmc null)")
         if strict is not None:
             strict["roofline"] = attention_roofline(strict.pop("_timers"), k32, False,
                                                     "HIP events around eager launches of the fp32 step right after its timed region",
@@ -913,8 +958,9 @@ def main():
                                       if graphed and stream is None else
                                       "device-to-device copy of each batch into its recording's buffers, inside the timed region" if graphed
                                       else "none (eager step reads the resident batch)")},
-            "roofline": roofline,
         }
+        if roofline is not None:
+            result["roofline"] = roofline
         if balance_note is not None:
             result["config"].update(balance_note)
         if per_rank is not None:
@@ -933,12 +979,12 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if not args.no_gather:
+        if args.full and not args.no_gather:
             result["gather_roofline"] = gather_microbench(dev)
             result["projection_roofline"] = projection_microbench(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args.nodes, args.edges)
-        if world == 1 and not args.no_sample_loop and not args.mixed and not args.large:
+        if args.full and world == 1 and not args.no_sample_loop and not args.mixed and not args.large:
             result["sample_loop"] = sample_loop_bench(model, dev)
         print(json.dumps(result), flush=True)
 

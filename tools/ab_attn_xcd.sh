@@ -4,7 +4,7 @@
 # kernel durations of one eager step each (the bench line's roofline object).     gpurun -- bash tools/ab_attn_xcd.sh
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/r06_attn_xcd_ab.txt; : > $OUT
-ARGS="--steps 40 --warmup 5 --no-cpu-baseline --no-gather --no-strict --no-raster --no-sample-loop --sustain-seconds 0"
+ARGS="--full --steps 40 --warmup 5 --no-cpu-baseline --no-gather --no-strict --no-raster --no-sample-loop --sustain-seconds 0"
 for rep in 1 2 3; do
   for lib in shipped noxcd; do
     if [ $lib = shipped ]; then CMD="python3 $R/bench.py $ARGS"; else CMD="python3 $R/tools/run_with_lib.py $R/dgdm_histopath_lab_amd/lib/noxcd/libdgdm_hip.so $R/bench.py $ARGS"; fi

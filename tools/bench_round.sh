@@ -4,10 +4,10 @@
 TAG=${1:-rXX}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out
-python3 $R/bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-python3 $R/bench.py --mixed --no-cpu-baseline --no-gather > $O/${TAG}_bench_mixed.json 2> $O/${TAG}_bench_mixed.err
-python3 $R/bench.py --large --no-cpu-baseline --no-gather --steps 10 --warmup 3 > $O/${TAG}_bench_large.json 2> $O/${TAG}_bench_large.err
-python3 $R/bench.py --large --pixel-positions 224 --no-cpu-baseline --no-gather --steps 10 --warmup 3 > $O/${TAG}_bench_large_raster.json 2> $O/${TAG}_bench_large_raster.err
+python3 $R/bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python3 $R/bench.py --full --mixed --no-cpu-baseline --no-gather > $O/${TAG}_bench_mixed.json 2> $O/${TAG}_bench_mixed.err
+python3 $R/bench.py --full --large --no-cpu-baseline --no-gather --steps 10 --warmup 3 > $O/${TAG}_bench_large.json 2> $O/${TAG}_bench_large.err
+python3 $R/bench.py --full --large --pixel-positions 224 --no-cpu-baseline --no-gather --steps 10 --warmup 3 > $O/${TAG}_bench_large_raster.json 2> $O/${TAG}_bench_large_raster.err
 for f in bench bench_mixed bench_large bench_large_raster; do
   python3 - "$O/${TAG}_$f.json" <<'PY'
 import json, sys

@@ -2,8 +2,8 @@
 """Per-kernel HBM traffic from two rocprofv3 --pmc passes (FETCH_SIZE and WRITE_SIZE cannot share a pass).
 
     (cd /tmp && export TMPDIR=/tmp && \
-     rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -- python3 $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline && \
-     rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -- python3 $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline)
+     rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -- python3 $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline && \
+     rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -- python3 $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline)
     python tools/pmc_traffic.py $OUT/fetch $OUT/write > profiles/rNN_pmc_traffic.json
 
 Units and gfx950 corrections as MI355X_MICROARCH.md (HBM section) prescribes: FETCH_SIZE / WRITE_SIZE are

@@ -3,7 +3,7 @@
 
     (cd /tmp && export TMPDIR=/tmp && rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY \
         SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE \
-        --kernel-trace --output-format csv -d $OUT -- python3 $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-gather --eager)
+        --kernel-trace --output-format csv -d $OUT -- python3 $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-gather --eager)
     python tools/pmc_valu.py $OUT > profiles/rNN_pmc_valu.json
 
 Units (MI355X_MICROARCH.md, per-instruction table): SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count QUAD-cycles summed

@@ -7,7 +7,7 @@ TAG=${1:-rXX}
 REPO=$(pwd); OUT=$REPO/gpurun_out; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_sl_$TAG && mkdir -p /tmp/prof_sl_$TAG
-rocprofv3 --kernel-trace --stats -d /tmp/prof_sl_$TAG/trace -o bench -- python3 $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-gather --no-strict --no-raster --sustain-seconds 0 \
+rocprofv3 --kernel-trace --stats -d /tmp/prof_sl_$TAG/trace -o bench -- python3 $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-gather --no-strict --no-raster --sustain-seconds 0 \
    > $OUT/${TAG}_sample_loop_bench_line.json 2> /tmp/prof_sl_$TAG/trace.err || { tail -5 /tmp/prof_sl_$TAG/trace.err; exit 1; }
 DB=$(find /tmp/prof_sl_$TAG/trace -name "*.db" | head -1)
 python3 - $DB > $OUT/${TAG}_sample_loop_kernel_stats.txt <<'PY'
